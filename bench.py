@@ -298,6 +298,32 @@ class HipDevice:
         return bench_ops.measure(self.dev, impl=self.impl, iters=20)
 
 
+DUMP_BYTES = 64_000_000     # --dump-outputs: at most this much in all; a larger output is written as a fixed, seeded sample
+DUMP_NAMES = ("out", "grad_fm0", "grad_fm1")
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BYTES, seed=0):
+    """Write the arrays a caller of the timed path receives as DIR/<name>.npy (float32).  If they exceed `budget` bytes
+    together, every array is cut to the same fraction of its elements, picked (flat indices, ascending) by a generator
+    seeded with `seed`: the same sample from run to run.  Returns {name: {shape, dtype, sampled, n}}."""
+    import numpy as np
+    directory = Path(directory)
+    directory.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, budget / total) if total else 1.0
+    rng = np.random.default_rng(seed)
+    info = {}
+    for name, a in arrays.items():
+        flat = a.reshape(-1)
+        n = flat.size if frac >= 1.0 else int(flat.size * frac)
+        if n < flat.size:
+            flat = flat[np.sort(rng.choice(flat.size, n, replace=False))]
+        np.save(directory / f"{name}.npy", flat.reshape(a.shape) if n == a.size else flat)
+        info[name] = {"shape": list(a.shape), "dtype": "float32", "sampled": n < a.size, "n": int(n)}
+    return info
+
+
 def run(args, device):
     """The rank skeleton: init, setup, W warmup steps, EXACTLY K timed steps between barriers,
     MAX over ranks, one JSON line on rank 0."""
@@ -358,6 +384,9 @@ def run(args, device):
         device.bwd(order[i])
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, nred, device.reduce_device())
+    # --dump-outputs: what the last timed step computed (forward output, both gradients), copied before anything below
+    # launches on the same buffers again
+    last_outputs = device.snapshot(order[-1]) if args.dump_outputs and rank == 0 else None
     # The per-kernel figures: the SAME K steps once more, with a HIP event in front of every kernel and one behind the
     # last (2 K + 1 records; a step's closing event is the next one's opening event).  kernels[] / roofline = the event
     # intervals; they add up to the wall time of THIS pass (asserted below), which is longer than the metric's: an event
@@ -558,6 +587,9 @@ def run(args, device):
                 cb = cpu_baseline(cfg, cnt, budget_s=args.cpu_baseline_multi_s, threads=max(1, host_threads() // world))
                 cb["sample"] += f" (rank 0 of {world}, 1/{world} of the host's threads; the per-GPU workload, not the {world}-GPU job)"
                 line["cpu_baseline"] = cb
+        if last_outputs is not None:
+            line["dump_outputs"] = {"dir": str(args.dump_outputs), "step": K - 1, "buffer_set": order[-1],
+                                    "arrays": dump_outputs(args.dump_outputs, {n: x.cpu().numpy() for n, x in zip(DUMP_NAMES, last_outputs)})}
         print(json.dumps(line), flush=True)
 
     if dist_on:
@@ -583,6 +615,10 @@ def parse_args(argv=None):
                     "(launch under torch.distributed.run --nproc-per-node 1)")
     ap.add_argument("--backend", default="nccl", help="process-group backend: nccl = RCCL, one GPU per rank (the metric); gloo lets several "
                     "ranks REHEARSE the N > 1 path on one GPU (they share it: the line says so, its value is not a scaling figure)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (out, grad_fm0, grad_fm1) as DIR/<name>.npy, float32, "
+                         "<= 64 MB in all; beyond that each file holds a fixed, seeded sample of its array as a flat 1-D vector (the result line "
+                         "gives the full shape and sampled = true); the inputs depend only on the arguments")
     ap.add_argument("--settle-ms", type=float, default=SETTLE_MS, help="untimed steps until this much wall time has passed (clock settling)")
     return ap.parse_args(argv)
 

@@ -123,6 +123,7 @@ def test_fixtures_record_the_reference_sources_they_were_made_from():
     that oracle/_ref was compiled from when it was generated.  All fixtures agree; where /root/reference is mounted (the
     build container) the hashes are re-derived from the files as they lie there today."""
     import hashlib
+    import os
     from pathlib import Path
     from conftest import GOLDEN
     files = sorted(GOLDEN.glob("*.npz"))
@@ -139,5 +140,5 @@ def test_fixtures_record_the_reference_sources_they_were_made_from():
     for name, digest in listed.items():
         name = name.strip()
         path = root / name if name.startswith("oracle/") else ref / name
-        if path.exists():                                             # the reference is absent on the GPU box
+        if os.path.exists(path):                                      # the reference is absent (or unreadable) on most machines
             assert hashlib.sha256(path.read_bytes()).hexdigest() == digest, f"{name} changed since the fixtures were made"
