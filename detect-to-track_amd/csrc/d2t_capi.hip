@@ -68,7 +68,11 @@ extern "C" {
 static inline bool ws_misaligned_(const void* ws, size_t ws_bytes) { return ws && ws_bytes && (reinterpret_cast<uintptr_t>(ws) & 15u) != 0; }
 #define ws_misaligned(ws) ws_misaligned_(ws, ws_bytes)   /* checked only where a workspace is passed: ws_bytes = 0 never touches it */
 
-int d2t_version(void) { return 107; }   // 1.07: round 6 -- ROIPool forward k = 7 in the reference's own order (bit-identical, any number of RoIs); PSROIPool forward needs no workspace where it is one launch
+// 1.07: round 6 -- ROIPool forward k = 7 in the reference's own order (bit-identical); PSROIPool forward needs no workspace where it is one launch.
+// 1.08: the direct k = 7 ROIPool forward takes exactly the f32 calls with H, W <= 255 and H W 32 + 32 ceil(R / 65535) <= 160 KiB (its RoI
+//       share shrinks to the LDS the planes leave, d2t_roipool_fwd_direct.hip): those are bit-identical whatever R and C; other maps
+//       take the summed-area kernel (1e-5).  1.07 also sent R = 300, C = 1024 on 20 x 255 and R = 10^6 on 38 x 63 there.
+int d2t_version(void) { return 108; }
 
 #ifdef D2T_LAB_KERNELS
 int d2t_lab_build(void) { return 1; }   // present in the lab build only (lab/csrc/d2t_lab_selectors.h)

@@ -165,7 +165,9 @@ size_t direct_lds(int H, int W, int per) { return (size_t)H * W * RD_CG * 4 + (s
 // profiles/r06_ab_roipool_direct_cg16_lost.txt.)
 // RoI shares per channel group: about one workgroup per CU (one round) -- or two where two workgroups fit a CU's LDS together (38 x 63:
 // 79 KB each; config 3 30.6 against 31.4 us, while at 38 x 75, 91 KB, a second round of workgroups costs 64 against 58 us:
-// profiles/r06_roipool_direct_ab.txt) --, never more shares than 32-RoI pieces
+// profiles/r06_roipool_direct_ab.txt) --, never more shares than 32-RoI pieces.  Where that share's geometry does not fit the LDS the planes
+// leave (large maps: 20 x 255 holds 20 RoIs; many RoIs: 1,000,000 on 38 x 63), the share shrinks to what fits and the split grows, up to
+// the grid's 65535 -- so the kernel takes every map whose planes leave room for ceil(R / 65535) RoIs, whatever R and C.
 void direct_plan(int R, int C, int H, int W, int& gx, int& split, int& per)
 {
     gx = (C + RD_CG - 1) / RD_CG;
@@ -179,10 +181,18 @@ void direct_plan(int R, int C, int H, int W, int& gx, int& split, int& per)
     };
     plan(512);
     if (2 * direct_lds(H, W, per) > (size_t)LDS_MAX) plan(256);
+    const long long per_cap = ((long long)LDS_MAX - (long long)H * W * RD_CG * 4) / RD_GEO;   // RoIs whose geometry fits beside the planes
+    if (per_cap >= 1 && per > per_cap) {
+        const long long s = (R + per_cap - 1) / per_cap;
+        split = s > 65535 ? 65535 : (int)s;
+        per = (R + split - 1) / split;
+        split = (R + per - 1) / per;
+    }
 }
 
 }  // namespace
 
+// Exactly: k = 7, 1 <= H, W <= 255, H W 32 + 32 ceil(R / 65535) <= 160 KiB (direct_plan), and R C 49 < 2^31 - 1.
 bool roipool_fwd_direct_supported(int R, int C, int H, int W, int k)
 {
     if (!(k == KT && R >= 1 && C >= 1 && H >= 1 && W >= 1 && H <= 255 && W <= 255)) return false;

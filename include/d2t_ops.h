@@ -74,8 +74,9 @@ const char* d2t_error_string(int code);
  * pooling k = 7; float32.  Everything else -- and all of float64 -- runs type-generic kernels in the reference's order whose
  * results are bit-identical to the thread-per-element kernels D2T_IMPL_GENERIC selects (tested) -- with ONE exception: the float32
  * ROIPool forward with k <= 16, k != 7 and at least 32 RoIs runs the f64 summed-area kernel (within 1e-5 of the reference, NaN pattern exact;
- * tests/test_roipool.py::test_forward_any_bin_count_summed_area_tables; k = 7 itself is bit-identical since ABI 1.07:
- * d2t_roipool_fwd_direct.hip) -- in two tiers: the default
+ * tests/test_roipool.py::test_forward_any_bin_count_summed_area_tables; k = 7 itself is bit-identical -- since ABI 1.08 exactly where
+ * H <= 255, W <= 255 and H*W*32 + 32*ceil(R/65535) <= 160 KiB (the 8 interleaved planes of d2t_roipool_fwd_direct.hip leave LDS for the
+ * geometry of the RoI share), for any R and C the int32 guard admits; larger maps take the summed-area kernel too) -- in two tiers: the default
  * dispatch takes kernels that share the work the anchor repeats per thread (correlation f32, d_max <= 14: d2t_corr_fwd_mfma.hip /
  * d2t_corr_blocked.hip -- forward tiles with the FM1 window in LDS (d_max <= 8: on the f32 matrix pipe), backward four pixels x four
  * channels per thread from zero-padded row copies; pooling backward, k <= 32: d2t_pool_lists.hip -- per map row the lists of the bin rows / cells

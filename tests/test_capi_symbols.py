@@ -29,7 +29,8 @@ def test_symbol_exported(name, native):
 
 
 def test_version_and_error_strings(native):
-    assert native.version() >= 107                    # round 6: exact ROIPool forward, no workspace for the one-launch PSROIPool forward
+    assert native.version() >= 108                    # 1.07: exact ROIPool forward, no workspace for the one-launch PSROIPool forward;
+                                                      # 1.08: the direct ROIPool forward's RoI share fits the LDS the planes leave
     assert native.error_string(0) == b"ok"
     for code in (-1, -2, -3):
         assert native.error_string(code) and native.error_string(code) != b"ok"
@@ -107,3 +108,43 @@ def test_workspace_queries_round6(native):
     assert L.d2t_psroipool_fwd_workspace_bytes(3, 3, 20, 30, 7, 4) == 0           # small: thread-per-output kernel
     for R in (8, 300):
         assert L.d2t_roipool_fwd_workspace_bytes(R, 1891, 38, 75, 7, 4) == 0
+
+
+def test_workspace_queries_pin_the_offset_guard_edges(native):
+    """The tuned kernels' 32-bit offset guards, seen through the workspace queries (host arithmetic, no device): at each edge computed
+    from the predicate's formula (tests/test_size_envelope.py, which runs the kernels there) the query still gives the tuned design's
+    scratch, one step past it the next design's.  A moved constant in a predicate moves the transition and fails here."""
+    from test_size_envelope import corr_bwd_c_edge, corr_bwd_h_edge, corr_fwd_c_edge, psroipool_bwd_r_edge, roipool_bwd_c_edge
+    L, H, W, d, cells = native.lib, 38, 63, 8, 17 * 17
+    # corr_fwd_supported (d2t_corr_tuned.hip:587): the channel-split scratch of the tuned forward inside, nothing past it
+    C = corr_fwd_c_edge(H, W)
+    assert C == 224_128
+    for B in (1, 2):
+        assert L.d2t_corr_fwd_workspace_bytes(B, C, H, W, d, 1, 4) > 0
+        assert L.d2t_corr_fwd_workspace_bytes(B, C + 1, H, W, d, 1, 4) == 0
+    # corr_bwd8_supported, offset bound (d2t_corr_bwd8.hip:491): no scratch for the strip kernel, gradOut by displaced pixel past it
+    C = corr_bwd_c_edge(H, W)
+    assert C == 224_192
+    assert L.d2t_corr_bwd_workspace_bytes(1, C, H, W, d, 1, 4) == 0
+    assert L.d2t_corr_bwd_workspace_bytes(1, C + 1, H, W, d, 1, 4) >= H * W * cells * 4
+    # corr_bwd8_supported, tiles_i <= 250 (d2t_corr_bwd8.hip:488)
+    Hx = corr_bwd_h_edge()
+    for Wx in (20, 63):
+        assert L.d2t_corr_bwd_workspace_bytes(1, 32, Hx, Wx, d, 1, 4) == 0
+        assert L.d2t_corr_bwd_workspace_bytes(1, 32, Hx + 1, Wx, d, 1, 4) >= (Hx + 1) * Wx * cells * 4
+    # roipool_bwd_mfma_supported (d2t_pool_bwd.hip:532): the GEMM form's row lists inside, the pixel form's transposed gradOut past it
+    R = 4000
+    C = roipool_bwd_c_edge(R)
+    assert C == 5478
+    assert L.d2t_roipool_bwd_workspace_bytes(R, C, H, W, 7, 4) < R * C * 49 * 4 // 8
+    assert L.d2t_roipool_bwd_workspace_bytes(R, C + 1, H, W, 7, 4) >= R * (C + 1) * 49 * 4
+    # psroipool_bwd_rows_supported (d2t_pool_bwd.hip:1413): the rows design's scratch (one set of planes, 15 MB here) hides under the bin
+    # table every design shares (R 49 16 bytes); past the edge (rows and GEMM out) the next design's planes come on top of that table
+    nT = 32
+    R = psroipool_bwd_r_edge(nT)
+    assert R == 342_392
+    planes = nT * 49 * H * W * 4
+    inside = L.d2t_psroipool_bwd_workspace_bytes(R, nT, H, W, 7, 4)
+    past = L.d2t_psroipool_bwd_workspace_bytes(R + 1, nT, H, W, 7, 4)
+    assert R * 49 * 16 <= inside < R * 49 * 16 + planes
+    assert past >= (R + 1) * 49 * 16 + planes

@@ -106,7 +106,8 @@ def test_matches_oracle(case, dtype, impl, oracle):
         pytest.skip("the tuned kernels are f32 (forward: k <= 16; backward: k = 7, else the bin lists)")
     out = _n(_ext.roipool_forward(_t(fm), _t(rois), k, impl))
     # round 6: k = 7 runs d2t_roipool_fwd_direct.hip (the reference's order: bit-identical); the summed-area tables (within 1e-5) serve k != 7
-    direct = k == 7 and H * W * 32 + 4800 <= 160 * 1024           # (maps whose 8 interleaved planes fit the LDS)
+    # (maps whose 8 interleaved planes leave LDS for the geometry of ceil(R / 65535) RoIs: roipool_fwd_direct_supported, include/d2t_ops.h)
+    direct = k == 7 and H <= 255 and W <= 255 and H * W * 32 + 32 * -(-R // 65535) <= 160 * 1024
     sat_fwd = dtype == np.float32 and k <= 16 and not direct and (impl == 2 or (impl == 0 and R >= 32))
     _assert_fwd(out, oracle.roipool_fwd(fm, rois, k), exact=not sat_fwd)
     gin = _n(_ext.roipool_backward(_t(gout), _t(rois), H, W, impl))
