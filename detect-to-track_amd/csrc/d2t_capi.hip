@@ -72,7 +72,7 @@ static inline bool ws_misaligned_(const void* ws, size_t ws_bytes) { return ws &
 // 1.08: the direct k = 7 ROIPool forward takes exactly the f32 calls with H, W <= 255 and H W 32 + 32 ceil(R / 65535) <= 160 KiB (its RoI
 //       share shrinks to the LDS the planes leave, d2t_roipool_fwd_direct.hip): those are bit-identical whatever R and C; other maps
 //       take the summed-area kernel (1e-5).  1.07 also sent R = 300, C = 1024 on 20 x 255 and R = 10^6 on 38 x 63 there.
-int d2t_version(void) { return 108; }
+int d2t_version(void) { return 109; }
 
 #ifdef D2T_LAB_KERNELS
 int d2t_lab_build(void) { return 1; }   // present in the lab build only (lab/csrc/d2t_lab_selectors.h)
@@ -481,6 +481,54 @@ int d2t_region_filter_batched_f32(const float* anchors, const float* offsets, co
     if (!ws || ws_bytes < (size_t)N * region_filter_ws_bytes(A, max_dets)) return D2T_EWS;
     return region_filter_f32(anchors, offsets, confs, A, conf_thresh, max_dets, iou_thresh, out_boxes, out_conf, out_idx, out_count,
                              ws, as_stream(stream), N);
+}
+
+// ------------------------------------------------------------------ tubelet linking (reference viterbi.py)
+size_t d2t_link_workspace_bytes(int n_nodes, int max_tracks)
+{
+    if (n_nodes < 0 || max_tracks < 0) return 0;
+    const size_t a = link_scores_ws_bytes(n_nodes, max_tracks), b = link_paths_ws_bytes(n_nodes);
+    return a > b ? a : b;
+}
+
+int d2t_link_scores_f32(const float* confs, const float* boxes, const int32_t* det_off, const int32_t* frame_off,
+                        const float* tracks, const int32_t* track_off, const int64_t* mat_off, float iou_thresh,
+                        int P, int F, int N, int n_tracks, int64_t M, int max_dets, int max_tracks,
+                        double* scores, int32_t* status, void* ws, size_t ws_bytes, d2t_stream_t stream)
+{
+    if (P < 0 || F < P || N < 0 || n_tracks < 0 || M < 0 || max_dets < 0 || max_tracks < 0) return D2T_EINVAL;
+    if (P > 0 && F < 1) return D2T_EINVAL;
+    if (max_dets > D2T_LINK_MAX_DETS || max_tracks > D2T_LINK_MAX_TRACKS) return D2T_ETOOBIG;
+    if (!status || (P > 0 && (!det_off || !frame_off))) return D2T_EINVAL;
+    const int npairs = F - P;
+    if (npairs > 0 && (!track_off || !mat_off || (N > 0 && (!confs || !boxes)) || (n_tracks > 0 && !tracks) || (M > 0 && !scores)))
+        return D2T_EINVAL;
+    if (((reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(tracks) | reinterpret_cast<uintptr_t>(ws)) & 15) != 0)
+        return D2T_EINVAL;
+    if (!fits_i32(4LL * N) || !fits_i32(4LL * n_tracks)) return D2T_ETOOBIG;
+    if (npairs > 0 && link_scores_ws_bytes(N, max_tracks) > 0 && (!ws || ws_bytes < link_scores_ws_bytes(N, max_tracks))) return D2T_EWS;
+    return link_scores_f32(confs, boxes, det_off, frame_off, tracks, track_off, reinterpret_cast<const long long*>(mat_off), iou_thresh,
+                           P, F, N, n_tracks, M, max_dets, max_tracks, scores, status, ws, as_stream(stream));
+}
+
+int d2t_link_paths_f64(const double* scores, const int64_t* mat_off, const double* init, const int32_t* det_off,
+                       const int32_t* frame_off, int P, int F, int N, int64_t M, int max_dets, int max_frames, int max_paths,
+                       int32_t* out_start, int32_t* out_len, double* out_score, int32_t* out_nodes,
+                       int32_t* count, int32_t* status, void* ws, size_t ws_bytes, d2t_stream_t stream)
+{
+    if (P < 0 || F < P || N < 0 || M < 0 || max_dets < 0 || max_frames < 0 || (max_paths != 0 && max_paths != 1)) return D2T_EINVAL;
+    if (P > 0 && F < 1) return D2T_EINVAL;
+    if (max_dets > D2T_LINK_MAX_DETS || max_frames > D2T_LINK_MAX_FRAMES) return D2T_ETOOBIG;
+    if (P == 0) return D2T_OK;
+    if (!det_off || !frame_off || !count || !status) return D2T_EINVAL;
+    if (F > P && !mat_off) return D2T_EINVAL;
+    if (M > 0 && !scores) return D2T_EINVAL;
+    if (N > 0 && (!out_start || !out_len || !out_score || !out_nodes)) return D2T_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return D2T_EINVAL;
+    if (!fits_i32(8LL * N)) return D2T_ETOOBIG;
+    if (N > 0 && (!ws || ws_bytes < link_paths_ws_bytes(N))) return D2T_EWS;
+    return link_paths_f64(scores, reinterpret_cast<const long long*>(mat_off), init, det_off, frame_off, P, F, N, M, max_dets,
+                          max_frames, max_paths, out_start, out_len, out_score, out_nodes, count, status, ws, as_stream(stream));
 }
 
 }  // extern "C"

@@ -64,4 +64,15 @@ int region_filter_f32(const float* anchors, const float* offsets, const float* c
                       float conf_thresh, int max_dets, float iou_thresh,
                       float* out_boxes, float* out_conf, int* out_idx, int* out_count, void* ws, hipStream_t st, int N = 1);
 
+// ---- tubelet linking (d2t_link.hip): link scores of adjacent frames + repeated Viterbi extraction, one workgroup per problem
+size_t link_scores_ws_bytes(int n_nodes, int max_tracks);
+size_t link_paths_ws_bytes(int n_nodes);
+int link_scores_f32(const float* confs, const float* boxes, const int* det_off, const int* frame_off, const float* tracks,
+                    const int* track_off, const long long* mat_off, float iou_thresh, int P, int F, int N, int n_tracks,
+                    long long M, int max_dets, int max_tracks, double* scores, int* status, void* ws, hipStream_t st);
+int link_paths_f64(const double* scores, const long long* mat_off, const double* init, const int* det_off, const int* frame_off,
+                   int P, int F, int N, long long M, int max_dets, int max_frames, int max_paths,
+                   int* out_start, int* out_len, double* out_score, int* out_nodes, int* out_count, int* out_status,
+                   void* ws, hipStream_t st);
+
 }  // namespace d2t

@@ -14,6 +14,7 @@
 //   NMS                 greedy, in descending confidence: a kept box removes every later box with IoU > iou_thresh
 // Boxes are (centre_i, centre_j, height, width) fractions of the frame, as everywhere in the reference.
 #include "d2t_kernels.hpp"
+#include "d2t_iou.hpp"
 
 #include <type_traits>
 namespace d2t {
@@ -90,8 +91,6 @@ __device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned& t
     total = tot;
     return base + incl - v;
 }
-
-__device__ __forceinline__ bool iou_exceeds(const float4& a, const float4& b, float thr);
 
 // The greedy decision of one block of 64 boxes, by ONE wave.  `diag`: lane r holds row r's word of the block itself;
 // rem: the block's word of the removed set.  Everything in the chain is wave-uniform, so it is kept in SGPRs
@@ -348,21 +347,6 @@ k_region_topk(const unsigned* __restrict__ keys, const float* __restrict__ boxes
         }
         if (lane == 0) *out_count = kept;
     }
-}
-
-// IoU(a, b) > thr, decided as the float quotient inter / uni would decide it (oracle/regions.py: float32 throughout).
-// The quotient is first estimated with v_rcp_f32 (error of a few 1e-7 for a value in [0, 1]); the IEEE division runs
-// only when the estimate is within 1e-6 of the threshold or not a number (uni <= 0: the pair scores 0).
-__device__ __forceinline__ bool iou_exceeds(const float4& a, const float4& b, float thr)
-{
-    const float ai0 = a.x - a.z / 2.f, ai1 = a.x + a.z / 2.f, aj0 = a.y - a.w / 2.f, aj1 = a.y + a.w / 2.f;
-    const float bi0 = b.x - b.z / 2.f, bi1 = b.x + b.z / 2.f, bj0 = b.y - b.w / 2.f, bj1 = b.y + b.w / 2.f;
-    const float ih = fminf(ai1, bi1) - fmaxf(ai0, bi0), iw = fminf(aj1, bj1) - fmaxf(aj0, bj0);
-    const float inter = (ih > 0.f ? ih : 0.f) * (iw > 0.f ? iw : 0.f);
-    const float uni = a.z * a.w + b.z * b.w - inter;
-    const float q = inter * __builtin_amdgcn_rcpf(uni);
-    if (uni > 0.f && fabsf(q - thr) > 1e-6f && q <= 2.f) return q > thr;   // (q <= 2: its error stays below the margin)
-    return (uni > 0.f ? inter / uni : 0.f) > thr;
 }
 
 // mask[i][w] bit j: box 64w+j comes later than box i and overlaps it by more than `iou`

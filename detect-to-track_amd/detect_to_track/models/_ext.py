@@ -406,3 +406,81 @@ def region_filter_batched(anchors: Tensor, offsets: Tensor, confs: Tensor, conf_
                                                        count.data_ptr(), _ptr(ws), n, _stream(anchors))
     _native.check(rc, "region_filter_batched")
     return boxes, conf, idx, count
+
+
+# --------------------------------------------------------------------------- tubelet linking
+def _i32(t: Tensor, name: str) -> None:
+    _check_input(t, name)
+    if t.dtype != torch.int32:
+        raise TypeError(f"{name} must be int32, got {t.dtype}")
+
+
+def link_scores(confs: Tensor, boxes: Tensor, det_off: Tensor, frame_off: Tensor, tracks: Tensor, track_off: Tensor,
+                mat_off: Tensor, iou_thresh: float, M: int, max_dets: int, max_tracks: int):
+    """Link scores of every adjacent frame pair of P problems (reference viterbi.py:11-42, compute_link_scores, for all pairs
+    at once; include/d2t_ops.h, linking section, for the layout).  confs (N,), boxes (N,4), tracks (NT,4): float32 CUDA;
+    det_off (F+1,), frame_off (P+1,), track_off (F-P+1,) int32 and mat_off (F-P,) int64 CUDA.  Returns (scores (M,) float64,
+    status (1,) int32).  max_dets / max_tracks are the caller's bounds on detections per frame / tracks per pair."""
+    for t, name in ((confs, "confs"), (boxes, "boxes"), (tracks, "tracks")):
+        _check_input(t, name)
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+    for t, name in ((det_off, "det_off"), (frame_off, "frame_off"), (track_off, "track_off")):
+        _i32(t, name)
+    _check_input(mat_off, "mat_off")
+    if mat_off.dtype != torch.int64:
+        raise TypeError(f"mat_off must be int64, got {mat_off.dtype}")
+    N, F, P, NT = int(confs.numel()), int(det_off.numel()) - 1, int(frame_off.numel()) - 1, int(tracks.shape[0])
+    if tuple(boxes.shape) != (N, 4) or tracks.dim() != 2 or tracks.shape[1] != 4 or int(track_off.numel()) != F - P + 1 \
+            or int(mat_off.numel()) != F - P:
+        raise ValueError("link_scores: inconsistent layout (see include/d2t_ops.h, linking section)")
+    dev = confs.device
+    with torch.cuda.device(dev):
+        scores = torch.empty((int(M),), dtype=torch.float64, device=dev)
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        ws, n = _workspace(_native.lib.d2t_link_workspace_bytes(N, int(max_tracks)), confs)
+        rc = _native.lib.d2t_link_scores_f32(confs.data_ptr(), boxes.data_ptr(), det_off.data_ptr(), frame_off.data_ptr(),
+                                             _ptr(tracks if NT else None), track_off.data_ptr(), _ptr(mat_off if F > P else None),
+                                             float(iou_thresh), P, F, N, NT, int(M), int(max_dets), int(max_tracks),
+                                             _ptr(scores if M else None), status.data_ptr(), _ptr(ws), n, _stream(confs))
+    _native.check(rc, "link_scores")
+    return scores, status
+
+
+def link_paths(scores: Tensor, mat_off: Tensor, init, det_off: Tensor, frame_off: Tensor, max_dets: int, max_frames: int,
+               max_paths: int = 0):
+    """Viterbi extraction for P problems in one launch (reference viterbi.py:71-159; max_paths = 1: viterbi, 0: viterbi_multi_link).
+    scores (M,) float64, mat_off (F-P,) int64, init (N,) float64 or None (zeros), det_off (F+1,), frame_off (P+1,) int32: CUDA.
+    Returns (start, length, score, nodes, count, status): (N,) int32 / int32 / float64 / int32, then (P,) int32 twice; problem p's
+    paths sit at its node range [det_off[frame_off[p]], det_off[frame_off[p+1]]) (include/d2t_ops.h, linking section)."""
+    _check_input(scores, "scores")
+    if scores.dtype != torch.float64:
+        raise TypeError(f"scores must be float64, got {scores.dtype}")
+    _check_input(init, "init")
+    if init.dtype != torch.float64:
+        raise TypeError(f"init must be float64, got {init.dtype}")
+    _i32(det_off, "det_off")
+    _i32(frame_off, "frame_off")
+    _check_input(mat_off, "mat_off")
+    if mat_off.dtype != torch.int64:
+        raise TypeError(f"mat_off must be int64, got {mat_off.dtype}")
+    F, P, M = int(det_off.numel()) - 1, int(frame_off.numel()) - 1, int(scores.numel())
+    if int(mat_off.numel()) != F - P:
+        raise ValueError("link_paths: mat_off must hold one offset per frame pair")
+    dev = det_off.device
+    N = int(init.numel())
+    with torch.cuda.device(dev):
+        start = torch.empty((N,), dtype=torch.int32, device=dev)
+        length = torch.empty((N,), dtype=torch.int32, device=dev)
+        score = torch.empty((N,), dtype=torch.float64, device=dev)
+        nodes = torch.empty((N,), dtype=torch.int32, device=dev)
+        count = torch.empty((P,), dtype=torch.int32, device=dev)
+        status = torch.empty((P,), dtype=torch.int32, device=dev)
+        ws, n = _workspace(_native.lib.d2t_link_workspace_bytes(N, 0), det_off)
+        rc = _native.lib.d2t_link_paths_f64(_ptr(scores if M else None), _ptr(mat_off if F > P else None), _ptr(init if N else None),
+                                            det_off.data_ptr(), frame_off.data_ptr(), P, F, N, M, int(max_dets), int(max_frames),
+                                            int(max_paths), _ptr(start if N else None), _ptr(length if N else None),
+                                            _ptr(score if N else None), _ptr(nodes if N else None), count.data_ptr(), status.data_ptr(),
+                                            _ptr(ws), n, _stream(det_off))
+    _native.check(rc, "link_paths")
+    return start, length, score, nodes, count, status

@@ -92,6 +92,16 @@ _proto("d2t_region_filter_f32", _I, [_P, _P, _P, _I, ctypes.c_float, _I, ctypes.
 # (anchors, offsets, confs, N, A, conf_thresh, max_dets, iou_thresh, out_boxes, out_conf, out_idx, out_count, ws, ws_bytes, stream)
 _proto("d2t_region_filter_batched_f32", _I, [_P, _P, _P, _I, _I, ctypes.c_float, _I, ctypes.c_float, _P, _P, _P, _P, _P, _Z, _P])
 SYMBOLS += ["d2t_region_filter_workspace_bytes", "d2t_region_filter_f32", "d2t_region_filter_batched_f32"]
+# tubelet linking: (n_nodes, max_tracks) ;
+# (confs, boxes, det_off, frame_off, tracks, track_off, mat_off, iou_thresh, P, F, N, n_tracks, M, max_dets, max_tracks, scores, status, ws, ws_bytes, stream)
+# (scores, mat_off, init, det_off, frame_off, P, F, N, M, max_dets, max_frames, max_paths, start, len, score, nodes, count, status, ws, ws_bytes, stream)
+_LL = ctypes.c_longlong
+_proto("d2t_link_workspace_bytes", _Z, [_I, _I])
+_proto("d2t_link_scores_f32", _I, [_P] * 7 + [ctypes.c_float, _I, _I, _I, _I, _LL, _I, _I, _P, _P, _P, _Z, _P])
+_proto("d2t_link_paths_f64", _I, [_P] * 5 + [_I, _I, _I, _LL, _I, _I, _I] + [_P] * 7 + [_Z, _P])
+SYMBOLS += ["d2t_link_workspace_bytes", "d2t_link_scores_f32", "d2t_link_paths_f64"]
+LINK_MAX_DETS, LINK_MAX_TRACKS, LINK_MAX_FRAMES = 1024, 1024, 8192                     # include/d2t_ops.h
+LINK_OK, LINK_NONTERMINATING, LINK_EMPTY, LINK_BAD_LAYOUT, LINK_INTERNAL = 0, 1, 2, 3, 4
 _proto("d2t_psroipool_channels", _I, [_P, _I, _I, _P])
 _proto("d2t_corr_mask", _I, [_P, _I, _I, _I, _I, _P])
 SYMBOLS += ["d2t_psroipool_channels", "d2t_corr_mask"]

@@ -245,6 +245,62 @@ int d2t_region_filter_batched_f32(const float* anchors, const float* offsets, co
                                   float* out_boxes, float* out_conf, int32_t* out_idx, int32_t* out_count,
                                   void* ws, size_t ws_bytes, d2t_stream_t stream);
 
+/* ---------------- tubelet linking: Viterbi over detections and tracks, many problems per call ----------------
+ * The step that turns per-frame detections and the tracker's boxes into tubelets (reference detect_to_track/viterbi.py:
+ * compute_link_scores :11, compute_score_seq :45, viterbi :71, viterbi_multi_link :119, viterbi_tracking :162), on the
+ * device, for P independent problems (one per video and class) in one call.  Results equal the reference's bit for bit:
+ * the same paths in the same order with the same float64 scores.
+ *
+ * Ragged layout (all int32 / int64 arrays are DEVICE arrays; the library checks every offset against the extents below
+ * before it uses it, and a problem whose offsets do not fit gets status D2T_LINK_BAD_LAYOUT and no output):
+ *   frame_off (P+1)   problem p owns frames [frame_off[p], frame_off[p+1]), at least 1; frame_off[P] = F
+ *   det_off   (F+1)   frame f owns nodes (detections) [det_off[f], det_off[f+1]); det_off[F] = N
+ *   pairs             problem p's frames t, t+1 form pair g = frame_off[p] - p + t; there are F - P pairs
+ *   track_off (F-P+1) pair g's tracks are [track_off[g], track_off[g+1]) of tracks (n_tracks,4)
+ *   mat_off   (F-P)   pair g's (D_t, D_t+1) row-major float64 matrix starts at scores + mat_off[g]; scores holds M elements
+ * Boxes and tracks are (centre_i, centre_j, height, width), float32, 16-byte aligned.
+ *
+ * Link scores: scores[g](a, b) = (double)(float)(confs[a] + confs[b]) + (psi ? 1.0 : 0.0), psi = some track t of the pair
+ * with IoU(a, t) > iou_thresh and IoU(b, t) > iou_thresh, IoU in float32 (the region filter's IoU decision).  *status
+ * (one int32) is 0 or D2T_LINK_BAD_LAYOUT.
+ *
+ * Paths: for each problem, max_paths = 0 runs viterbi_multi_link (every tubelet, in extraction order, then the one-node
+ * paths of the live frame-0 nodes with a finite init score), max_paths = 1 runs viterbi (the best path into the last
+ * frame).  init (N, may be NULL = zeros) is read at the frame-0 nodes.  scores may be any float64 matrices (-inf = no
+ * link); they are not written.  Outputs are indexed by the problem's node range [n0, n1) = [det_off[frame_off[p]],
+ * det_off[frame_off[p+1]]): path k of problem p is out_start / out_len / out_score[n0 + k] (frames start .. start+len-1),
+ * its frame-local node indices follow those of paths 0..k-1 in out_nodes[n0 + ...]; a problem has at most n1 - n0 paths
+ * and path nodes.  count (P) is the number of paths, status (P) one of D2T_LINK_*:
+ *   D2T_LINK_NONTERMINATING  an extraction's best final node was already removed: the reference repeats that extraction
+ *                            forever (e.g. all-zero scores).  The kernel stops the problem there.
+ *   D2T_LINK_EMPTY           max_paths = 1 and the last frame has no node (the reference's max() of nothing)
+ * Both calls are asynchronous and synchronise nothing.                                                            */
+#define D2T_LINK_MAX_DETS   1024   /* detections per frame (max_dets) */
+#define D2T_LINK_MAX_TRACKS 1024   /* tracks per frame pair (max_tracks) */
+#define D2T_LINK_MAX_FRAMES 8192   /* frames per problem (max_frames) */
+enum {
+    D2T_LINK_OK             = 0,
+    D2T_LINK_NONTERMINATING = 1,
+    D2T_LINK_EMPTY          = 2,
+    D2T_LINK_BAD_LAYOUT     = 3,
+    D2T_LINK_INTERNAL       = 4   /* a bound of the extraction loop was hit: never for a valid layout */
+};
+/* Scratch of either call for N nodes: 2 * N * ceil(max_tracks / 64) words of match bits (link scores) or N * 13 bytes of
+ * node state (paths), rounded up; 16-byte aligned. */
+size_t d2t_link_workspace_bytes(int n_nodes, int max_tracks);
+/* max_dets: the most nodes any frame has (<= D2T_LINK_MAX_DETS), max_tracks: the most tracks any pair has
+ * (<= D2T_LINK_MAX_TRACKS); D2T_ETOOBIG beyond them.  confs (N), boxes (N,4), tracks (n_tracks,4) float32. */
+int d2t_link_scores_f32(const float* confs, const float* boxes, const int32_t* det_off, const int32_t* frame_off,
+                        const float* tracks, const int32_t* track_off, const int64_t* mat_off, float iou_thresh,
+                        int P, int F, int N, int n_tracks, int64_t M, int max_dets, int max_tracks,
+                        double* scores, int32_t* status, void* ws, size_t ws_bytes, d2t_stream_t stream);
+/* max_frames: the most frames any problem has (<= D2T_LINK_MAX_FRAMES); max_paths 0 or 1.
+ * out_start, out_len, out_nodes (N) int32; out_score (N) float64; count, status (P) int32. */
+int d2t_link_paths_f64(const double* scores, const int64_t* mat_off, const double* init, const int32_t* det_off,
+                       const int32_t* frame_off, int P, int F, int N, int64_t M, int max_dets, int max_frames, int max_paths,
+                       int32_t* out_start, int32_t* out_len, double* out_score, int32_t* out_nodes,
+                       int32_t* count, int32_t* status, void* ws, size_t ws_bytes, d2t_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
